@@ -11,13 +11,16 @@ packed film.  A "step" = one launch of the hot path = one sample per pixel over 
 `transport` in the line says what moved the films: "rccl" (torch.distributed nccl backend or the library's ncclGather between distinct GPUs), "gloo" (ranks that
 had to share a GPU: host memory), "copy" (group members sharing a GPU: device-to-device copies), "none" (one rank).  `ranks_seen` / `devices_seen` are counted, not assumed.
 
-Timed region: EXACTLY `steps` steps, bracketed by barrier + synchronize on both sides, max over ranks.  The region is
-repeated `--repeats` times (default 5, SURVEY.md §8(d): "median of >= 5 runs") on a cleared sensor; `value` is the median
-repeat, every repeat is listed in `repeat_values`.
-After the headline (N = 1, S1, constant environment): `other_configs` = the same K-step batch on BASELINE.json's other single-GPU configurations — S2 (configs[4]: 10.24 M
+Timed region: EXACTLY `steps` steps, bracketed by barrier + synchronize on both sides, max over ranks.  A plain run times the region
+once and prints the headline (`value`, `ms_per_step`, rays, transport); `--dump-outputs DIR` writes the film the timed steps accumulated
+(DIR/film.npy, float32 (H, W, 4) — the array HdMoonshineGetSensorData hands a caller; a seeded sample of its pixels above 60 MiB).
+`--repeats R` (default 1; 5 under `--full`, SURVEY.md §8(d): "median of >= 5 runs") repeats the region on a cleared sensor: `value` is the
+median repeat, every repeat is listed in `repeat_values`.
+`--full` adds everything else, outside the timed region: the roofline (stream-order attribution pass, counting pass), `per_rank`, and,
+after the headline (N = 1, S1, constant environment): `other_configs` = the same K-step batch on BASELINE.json's other single-GPU configurations — S2 (configs[4]: 10.24 M
 instanced triangles), S1 under the image environment and the configs[2] stand-in (textured, GLB + PIZ EXR through the importers) — each in a context of its own, median of 3
 (`--no-other-configs` skips them; never the headline `value`); `--sustain-seconds S` (default 3): the batch back to back for >= S seconds (`sustained`: rate per 1-s window,
-shader clock probed while it runs; 0 = off).
+shader clock probed while it runs; 0 = off); `cpu_baseline` (`--no-cpu-baseline` skips it).
 """
 import argparse
 import json
@@ -38,6 +41,9 @@ from moonshine_amd.hostinfo import usable_cores, source_hash  # noqa: E402
 
 HBM_PEAK = 8.0e12  # B/s, /opt/skills/guides/MI355X_MICROARCH.md "HBM3E peak BW"
 KERNELS = ("k_trace_closest", "k_trace_shadow", "k_shade")
+# after the --warmup steps, one untimed batch shaped like the timed region (capped): the first region of a given batch size runs ~1 ms slower
+# than the ones after it (20 steps: 5700-5790 Mrays/s against 5890-5920), so without it a single timed region would measure that one-off
+SHAPE_WARMUP = 256
 
 
 _STANDIN = None
@@ -207,6 +213,7 @@ def run_group(a):
             torch.cuda.synchronize(d)
     if a.warmup:
         g.render(sensor, lens, launches=a.warmup)
+        g.render(sensor, lens, launches=min(a.steps, SHAPE_WARMUP))
     for c in g.members:
         c.reset_stats()
     times = []
@@ -222,8 +229,7 @@ def run_group(a):
     st = [c.stats() for c in g.members]
     closest, shadow, samples = (sum(float(s[k]) for s in st) / R for k in ("closest_rays", "shadow_rays", "samples"))
     rays, dt = closest + shadow, statistics.median(times)
-    if a.dump_film:
-        np.save(a.dump_film, g.sensor_data(sensor))
+    save_film(a, g.sensor_data(sensor) if (a.dump_film or a.dump_outputs) else None)
     rates = [rays / t / 1e6 for t in times]
     print(json.dumps({
         "metric": "Mrays/sec, 1M-tri scene @1080p" if a.scene == "s1" else ("Mrays/sec, 10M-tri instanced scene @1080p" if a.scene == "s2" else "Mrays/sec, 1M-tri textured interior (asset substituted) @1080p"),
@@ -235,6 +241,25 @@ def run_group(a):
         "msamples_per_s": samples / dt / 1e6, "rays": {"closest": closest, "shadow": shadow, "per_sample": rays / max(samples, 1.0)},
         "roofline": None, "cpu_baseline": None}))
     g.close()
+
+
+DUMP_BYTES = 60 << 20     # the .npy file stays under 64 MB (decimal), header included
+
+
+def save_film(a, film):
+    """--dump-film FILE: the film as is.  --dump-outputs DIR: DIR/film.npy, float32 (H, W, 4) — above DUMP_BYTES a fixed seeded sample of its
+    pixels (the same pixels at the same size in every run), so that two builds of the library can be compared value for value"""
+    if film is None:
+        return
+    if a.dump_film:
+        np.save(a.dump_film, film)
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        film = np.asarray(film, dtype=np.float32)
+        if film.nbytes > DUMP_BYTES:
+            px = film.reshape(-1, film.shape[-1])
+            film = px[np.sort(np.random.default_rng(0).choice(len(px), DUMP_BYTES // px[0].nbytes, replace=False))]
+        np.save(os.path.join(a.dump_outputs, "film.npy"), film)
 
 
 def workload_name(a):
@@ -252,8 +277,8 @@ def main():
                     help="how --gpus N > 1 runs when no launcher started us: ranks = child processes under torch.distributed.run (auto), group = MsneGroup in this process")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=4, help="untimed steps before the timed region, then one untimed batch of min(--steps, 256) steps (0: neither)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each, `value` = the median (default 1; 5 under --full)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--scene", default="s1", choices=["s1", "s2", "standin"])
@@ -264,7 +289,12 @@ def main():
                     help="after the timed repeats: back-to-back K-step batches for at least this long, reported as `sustained` (rate per 1-s window, shader clock at both ends); 0 = off")
     ap.add_argument("--no-gpu-visits", action="store_true", help="skip the extra pass that counts the GPU's own node visits / triangle tests per ray (profiling runs: its kernels would be counted)")
     ap.add_argument("--dump-film", default=None, help="rank 0 saves the assembled film of the last repeat here (.npy): parity tests of the gather path")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the timed steps computed (the film) as DIR/film.npy, float32, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: 5 repeats, the roofline passes, per_rank, sustained, other_configs, cpu_baseline (the --no-* / --sustain-seconds options act here)")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -328,6 +358,7 @@ def main():
 
     if a.warmup:
         ctx.render(sensor, lens, launches=a.warmup, readback=False)
+        ctx.render(sensor, lens, launches=min(a.steps, SHAPE_WARMUP), readback=False)
     gather()
     warm = ctx.stats()
     ctx.reset_stats()
@@ -345,26 +376,31 @@ def main():
         t_render.append(t1 - t0); t_gather.append(t2 - t1)           # this rank's own share: its K steps, then the gather (a sender returns once its film is handed over; rank 0 also unpacks)
     st = ctx.stats()          # sums over the repeats (every repeat traces the same rays: same sample indices)
     R = len(times)
-    # attribution pass (outside the timed region): the same K steps once more with the kernels in STREAM ORDER, so that each kernel's HIP-event
+    if rank == 0 and (a.dump_film or a.dump_outputs):
+        if world == 1:
+            ctx.render(sensor, lens, launches=0, readback=True)     # the gather already unpacked the film on rank 0 when world > 1
+        save_film(a, ctx.sensor_data(sensor))
+    # attribution pass (--full, outside the timed region): the same K steps once more with the kernels in STREAM ORDER, so that each kernel's HIP-event
     # duration is exclusive (in the timed repeats k_trace_shadow(b) overlaps k_trace_closest(b+1) on a second stream and both durations include
     # the other's share of the SIMDs).  The roofline's kernel and its launch durations come from this pass: they do not depend on --steps.
-    ctx.reset_stats(); ctx.set_profiling(kernel_events=2, traversal_counters=False)
-    ctx.clear_sensor(sensor); sync()
-    ctx.render(sensor, lens, launches=a.steps, readback=False)
-    sync()
-    sa = ctx.stats()
-    # ... and what each bounce of this rank's shard cost in that pass: launches arrive as closest(b), shade(b), shadow(b) per batch (moonshine_amd.h MsneGetLaunchTimes)
     NB = 8 + 2                                                         # max_bounces + 2 passes per batch (HdMoonshine::render max_iter)
-    per_bounce = {0: [0.0] * NB, 1: [0.0] * NB, 2: [0.0] * NB}; seen = {0: 0, 1: 0, 2: 0}
-    for kind, ms in ctx.launch_times():
-        per_bounce[kind][seen[kind] % (NB - 1 if kind == 1 else NB)] += ms; seen[kind] += 1
-    ctx.set_profiling(kernel_events=False, traversal_counters=False)
+    if a.full:
+        ctx.reset_stats(); ctx.set_profiling(kernel_events=2, traversal_counters=False)
+        ctx.clear_sensor(sensor); sync()
+        ctx.render(sensor, lens, launches=a.steps, readback=False)
+        sync()
+        sa = ctx.stats()
+        # ... and what each bounce of this rank's shard cost in that pass: launches arrive as closest(b), shade(b), shadow(b) per batch (moonshine_amd.h MsneGetLaunchTimes)
+        per_bounce = {0: [0.0] * NB, 1: [0.0] * NB, 2: [0.0] * NB}; seen = {0: 0, 1: 0, 2: 0}
+        for kind, ms in ctx.launch_times():
+            per_bounce[kind][seen[kind] % (NB - 1 if kind == 1 else NB)] += ms; seen[kind] += 1
+        ctx.set_profiling(kernel_events=False, traversal_counters=False)
 
     # ... and once more with the traversal kernels' COUNTING instantiations (outside the timed region, never part of `value`): the GPU's own node visits and triangle tests
     # per ray in THIS run — a quantity of the roofline object that is observed here and not read from a committed file (`roofline.gpu_visits`).  Plain device
     # synchronisation only: a rank that fails here must not leave the others in a barrier.
     gpu_visits = None
-    if not a.no_gpu_visits:
+    if a.full and not a.no_gpu_visits:
         try:
             ctx.reset_stats(); ctx.set_profiling(kernel_events=False, traversal_counters=True)
             ctx.clear_sensor(sensor); torch.cuda.synchronize()
@@ -384,7 +420,7 @@ def main():
     # runs back to back for at least S seconds.  Per-batch wall times give the rate per 1-s window; the shader clock is probed by one wave on a stream of its own
     # (MsneProbeClockGhz) from a second host thread while the batches run.
     sustained = None
-    if a.sustain_seconds > 0:
+    if a.full and a.sustain_seconds > 0:
         import threading
         clocks, stop = [], threading.Event()
 
@@ -441,27 +477,24 @@ def main():
         devices_seen = 1
     # every rank's own numbers, so that a scaling result below the prediction can be attributed from the one line: its K steps (median repeat), its gather, the
     # attribution pass by bounce — the thin late bounces of a small shard are where DESIGN.md section 7 expects the loss
-    mine = torch.tensor([statistics.median(t_render) * 1e3, statistics.median(t_gather) * 1e3, sa["render_ms"], float(st["closest_rays"] + st["shadow_rays"]) / R]
-                        + per_bounce[0] + per_bounce[2] + per_bounce[1], dtype=torch.float64, device="cuda")
-    if world > 1:
-        allr = [torch.empty_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-    else:
-        allr = [mine]
-    per_rank = [{"rank": r, "render_ms": float(v[0]), "gather_ms": float(v[1]), "render_ms_stream_order": float(v[2]), "rays": float(v[3]),
-                 "closest_ms_by_bounce": [round(float(x), 4) for x in v[4:4 + NB]], "shade_ms_by_bounce": [round(float(x), 4) for x in v[4 + NB:4 + 2 * NB]],
-                 "shadow_ms_by_bounce": [round(float(x), 4) for x in v[4 + 2 * NB:4 + 3 * NB - 1]]} for r, v in enumerate(allr)]
+    if a.full:
+        mine = torch.tensor([statistics.median(t_render) * 1e3, statistics.median(t_gather) * 1e3, sa["render_ms"], float(st["closest_rays"] + st["shadow_rays"]) / R]
+                            + per_bounce[0] + per_bounce[2] + per_bounce[1], dtype=torch.float64, device="cuda")
+        if world > 1:
+            allr = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+        else:
+            allr = [mine]
+        per_rank = [{"rank": r, "render_ms": float(v[0]), "gather_ms": float(v[1]), "render_ms_stream_order": float(v[2]), "rays": float(v[3]),
+                     "closest_ms_by_bounce": [round(float(x), 4) for x in v[4:4 + NB]], "shade_ms_by_bounce": [round(float(x), 4) for x in v[4 + NB:4 + 2 * NB]],
+                     "shadow_ms_by_bounce": [round(float(x), 4) for x in v[4 + 2 * NB:4 + 3 * NB - 1]]} for r, v in enumerate(allr)]
     closest, shadow, samples = float(tt[R]), float(tt[R + 1]), float(tt[R + 2])     # per repeat, all ranks
     ranks_seen = int(round(float(tt[R + 3])))                                         # ranks that took part in the reduction (counted, not assumed)
     rays = closest + shadow
     dt = statistics.median(times)
 
     observed_backend = dist.get_backend() if world > 1 else "none"
-    if rank == 0 and a.dump_film:
-        if world == 1:
-            ctx.render(sensor, lens, launches=0, readback=True)     # the gather already unpacked the film on rank 0 when world > 1
-        np.save(a.dump_film, ctx.sensor_data(sensor))
-    if rank == 0:
+    if rank == 0 and a.full:
         fx = json.load(open(os.path.join(ROOT, "tests", "golden", "roofline_%s.json" % a.scene)))
         # bytes per unit of each kernel: V_n * 80 + V_t * 48 + 48 with the kernel's OWN canonical visit counts;
         # k_shade: B_hit per surface hit + the 288 B of wavefront state it reads and writes per path
@@ -550,6 +583,20 @@ def main():
                 roof["traffic_frac"] = roof["traffic"] / (avg_ms * 1e-3) / HBM_PEAK
             if "memory_pipeline" in ck:
                 roof["memory_pipeline"] = dict(ck["memory_pipeline"], **{"from": "profiles/" + cnt_file})
+        full = {
+            "roofline": roof,
+            # per rank: wall time of its own K steps and of its gather in the median repeat; the stream-order pass by bounce (sums over the batch's launches of that bounce)
+            "per_rank": per_rank,
+            "whole_path_roofline_frac": (rays / dt * fx["B_ray"] + samples / dt * (fx["B_shade"] + 32)) / HBM_PEAK / world,
+            "kernel_ms_stream_order": {k: kms[k] for k in KERNELS}, "render_ms_stream_order": sa["render_ms"], "render_ms_per_repeat": st["render_ms"] / R,
+            "kernel_hbm_algorithmic_frac": {k: unit_bytes[k] * kun[k] / max(kms[k] * 1e-3, 1e-12) / HBM_PEAK for k in KERNELS},
+            "kernel_valu_frac": ({k: valu_cycles(k) * kun[k] / max(kms[k] * 1e-3, 1e-12) / (1024.0e9 * ((cnt["kernels"][k].get("memory_pipeline") or {}).get("clock_ghz") or 2.4)) for k in KERNELS}
+                                 if (cnt and cal and all("valu_class_per_unit" in cnt["kernels"].get(k, {}) for k in KERNELS)) else None),
+            # for tools/profile_counters.py: what the counters of a rocprofv3 run of this command have to be divided by
+            "profile_totals": {"closest_rays": warm["closest_rays"] + st["closest_rays"] + sa["closest_rays"], "shadow_rays": warm["shadow_rays"] + st["shadow_rays"] + sa["shadow_rays"],
+                               "samples": warm["samples"] + st["samples"] + sa["samples"]},
+        }
+    if rank == 0:
         rates = [rays / t / 1e6 for t in times]
         out = {
             "metric": "Mrays/sec, 1M-tri scene @1080p" if a.scene == "s1" else ("Mrays/sec, 10M-tri instanced scene @1080p" if a.scene == "s2" else "Mrays/sec, 1M-tri textured interior (asset substituted) @1080p"),
@@ -564,25 +611,17 @@ def main():
             "repeats": R, "repeat_values": rates, "spread": (max(rates) - min(rates)) / statistics.median(rates),
             "msamples_per_s": samples / dt / 1e6,
             "rays": {"closest": closest, "shadow": shadow, "per_sample": rays / max(samples, 1.0)},
-            "roofline": roof, "build": build_ms,
-            # per rank: wall time of its own K steps and of its gather in the median repeat; the stream-order pass by bounce (sums over the batch's launches of that bounce)
-            "per_rank": per_rank,
-            "whole_path_roofline_frac": (rays / dt * fx["B_ray"] + samples / dt * (fx["B_shade"] + 32)) / HBM_PEAK / world,
-            "kernel_ms_stream_order": {k: kms[k] for k in KERNELS}, "render_ms_stream_order": sa["render_ms"], "render_ms_per_repeat": st["render_ms"] / R,
-            "kernel_hbm_algorithmic_frac": {k: unit_bytes[k] * kun[k] / max(kms[k] * 1e-3, 1e-12) / HBM_PEAK for k in KERNELS},
-            "kernel_valu_frac": ({k: valu_cycles(k) * kun[k] / max(kms[k] * 1e-3, 1e-12) / (1024.0e9 * ((cnt["kernels"][k].get("memory_pipeline") or {}).get("clock_ghz") or 2.4)) for k in KERNELS}
-                                 if (cnt and cal and all("valu_class_per_unit" in cnt["kernels"].get(k, {}) for k in KERNELS)) else None),
-            # for tools/profile_counters.py: what the counters of a rocprofv3 run of this command have to be divided by
-            "profile_totals": {"closest_rays": warm["closest_rays"] + st["closest_rays"] + sa["closest_rays"], "shadow_rays": warm["shadow_rays"] + st["shadow_rays"] + sa["shadow_rays"],
-                               "samples": warm["samples"] + st["samples"] + sa["samples"]},
+            "build": build_ms,
         }
-        if sustained is not None:
-            out["sustained"] = sustained     # rank 0's clock over the whole job's rays (at N > 1 every rank runs the same number of batches, gather included)
-        if world == 1 and a.scene == "s1" and a.env == "constant" and not a.no_other_configs:
-            # the other single-GPU configurations of BASELINE.json, measured after the headline (a second or two): configs[4] (S2) and S1 under the image environment
-            out["other_configs"] = {"s2": other_config(a, dev, "s2", "constant"), "s1_sky": other_config(a, dev, "s1", "sky"), "standin": other_config(a, dev, "standin", "image")}
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a)
+        if a.full:
+            out.update(full)
+            if sustained is not None:
+                out["sustained"] = sustained     # rank 0's clock over the whole job's rays (at N > 1 every rank runs the same number of batches, gather included)
+            if world == 1 and a.scene == "s1" and a.env == "constant" and not a.no_other_configs:
+                # the other single-GPU configurations of BASELINE.json, measured after the headline (a second or two): configs[4] (S2) and S1 under the image environment
+                out["other_configs"] = {"s2": other_config(a, dev, "s2", "constant"), "s1_sky": other_config(a, dev, "s1", "sky"), "standin": other_config(a, dev, "standin", "image")}
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(a)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

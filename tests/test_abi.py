@@ -1,6 +1,7 @@
 """CPU tests: the C-ABI library loads and exports every symbol include/moonshine_amd.h declares; struct layouts match
 hydra/moonshine.h.  No compute call is made (there is no GPU here, and there is no CPU fallback)."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -90,15 +91,66 @@ def test_product_never_imports_the_oracle():
                     assert not pat.search(src), (f, pat.search(src).group(0))
 
 
-REF_HEADER = "/root/reference/hydra/moonshine.h"
+def canonical_decls(text):
+    """The declarations of a C header as data: handle typedefs, opaque structs, struct fields, enum members and function signatures (parameter
+    names dropped), comments and spacing ignored, sorted.  tests/golden/hydra_abi.json holds the SHA-256 of this form of the reference's
+    hydra/moonshine.h."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+
+    def norm(t):
+        return re.sub(r"\s*\*\s*", "*", " ".join(t.split()))
+    out = [["typedef", m.group(1), m.group(2)] for m in re.finditer(r"typedef\s+(\w+)\s+(\w+)\s*;", text)]
+    out += [["opaque", m.group(1), m.group(2)] for m in re.finditer(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;", text)]
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = []
+        for decl in m.group(2).split(";"):
+            if decl.strip():
+                ty, names = re.match(r"\s*(.*?)\s+(\w+(?:\s*,\s*\w+)*)\s*$", decl, flags=re.S).groups()
+                fields += [[norm(ty), n.strip()] for n in names.split(",")]
+        out.append(["struct", m.group(1), m.group(3), fields])
+    for m in re.finditer(r"typedef\s+enum\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        out.append(["enum", m.group(1), m.group(3), [e.strip() for e in m.group(2).split(",") if e.strip()]])
+    for m in re.finditer(r"(?:extern\s+\"C\"\s+)?([A-Za-z_][\w\s*]*?)\s*\b(HdMoonshine\w+)\s*\(([^;{]*)\)\s*;", text):
+        params = []
+        for p in m.group(3).split(","):
+            toks = norm(p).replace("*", " * ").split()
+            if len(toks) >= 2 and re.fullmatch(r"[A-Za-z_]\w*", toks[-1]) and toks[-2] != "const":
+                toks = toks[:-1]                  # a parameter name
+            t = norm(" ".join(toks))
+            if t and t != "void":
+                params.append(t)
+        out.append(["function", norm(m.group(1)), m.group(2), params])
+    return sorted(out, key=json.dumps)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_HEADER), reason="needs the reference checkout (not present on the GPU box)")
+def test_canonical_decls_sees_every_change_of_a_declaration():
+    """the canonical form keeps what a caller compiles against: a changed parameter type, field, enum member or return type changes it; comments,
+    spacing and parameter names do not"""
+    base = '''typedef uint32_t MeshHandle; typedef struct F32x2 { float x, y; } F32x2; typedef enum TextureFormat { f16x4, u8x4_srgb } TextureFormat;
+    typedef struct HdMoonshine HdMoonshine; extern "C" MeshHandle HdMoonshineCreateMesh(HdMoonshine*, const F32x2*, size_t);'''
+    same = base.replace("const F32x2*, size_t)", "const F32x2 * texcoords /* face-varying */, size_t count)").replace("{ float x, y; }", "{\n    float x,\n    y;\n}")
+    assert canonical_decls(same) == canonical_decls(base)
+    for a, b in (("size_t)", "uint32_t)"), ("const F32x2*", "F32x2*"), ("float x, y;", "double x, y;"), ("u8x4_srgb }", "u8x4_srgb, f32x4 }"),
+                 ("extern \"C\" MeshHandle", "extern \"C\" ImageHandle"), ("float x, y;", "float y, x;")):
+        assert canonical_decls(base.replace(a, b)) != canonical_decls(base), (a, b)
+    assert len([d for d in canonical_decls(base) if d[0] == "function"]) == 1
+
+
 def test_translation_unit_built_against_the_reference_header_links_and_loads(tmp_path, gpu_api):
-    """drop-in at the link level: a C++ file that sees ONLY the reference's hydra/moonshine.h (the header hydra/*.cpp
-    include) and calls all 24 entry points links against libmoonshine_amd.so and starts (nothing is executed: no GPU here)."""
+    """drop-in at the link level.  Part 1 of include/moonshine_amd.h declares exactly what the reference's hydra/moonshine.h (the header
+    hydra/*.cpp include) declares — its canonical form hashes to the value tests/golden/hydra_abi.json records for the reference header — so a
+    C++ file that calls all 24 entry points through those declarations compiles (-Wall -Werror), links against libmoonshine_amd.so and starts
+    (nothing is executed: no GPU here)."""
+    import hashlib
     import subprocess
     from moonshine_amd import build as b
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "hydra_abi.json")))
+    header = os.path.join(ROOT, "include", "moonshine_amd.h")
+    hdr = open(header, encoding="utf-8").read()
+    part1 = canonical_decls(hdr[hdr.index("Part 1 \u2014"):hdr.index("Part 2 \u2014")])
+    assert len(part1) == golden["declarations"] and len([d for d in part1 if d[0] == "function"]) == golden["entry_points"]
+    assert hashlib.sha256(json.dumps(part1).encode()).hexdigest() == golden["sha256"], "part 1 of include/moonshine_amd.h no longer declares what hydra/moonshine.h declares"
     src = tmp_path / "hydra_tu.cpp"
     src.write_text('''#include "%s"
 int main(int argc, char** argv) {
@@ -123,9 +175,10 @@ int main(int argc, char** argv) {
     HdMoonshineDestroy(c);
     return ok && d ? 0 : 1;
 }
-''' % REF_HEADER)
+''' % header)
     exe = tmp_path / "hydra_tu"
     libdir = os.path.dirname(b.LIB)
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-o", str(exe), str(src), "-L" + libdir, "-lmoonshine_amd", "-Wl,-rpath," + libdir,
+    # -Wno-comment: the header's comments name paths like hydra/*.cpp (the library itself is built with the same flag)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-comment", "-o", str(exe), str(src), "-L" + libdir, "-lmoonshine_amd", "-Wl,-rpath," + libdir,
                            "-Wl,-rpath-link," + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")])
     assert subprocess.run([str(exe)], timeout=120).returncode == 0

@@ -2047,7 +2047,7 @@ def test_bench_gather_path_with_two_ranks(tmp_path):
     code runs with world > 1 and assembles the film a single rank renders"""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["--steps", "3", "--warmup", "1", "--repeats", "2", "--width", "328", "--height", "200", "--no-cpu-baseline", "--no-other-configs", "--sustain-seconds", "0.2"]
+    args = ["--full", "--steps", "3", "--warmup", "1", "--repeats", "2", "--width", "328", "--height", "200", "--no-cpu-baseline", "--no-other-configs", "--sustain-seconds", "0.2"]
     one, two = str(tmp_path / "one.npy"), str(tmp_path / "two.npy")
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dump-film", one] + args, capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-2000:]
@@ -2077,7 +2077,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MSNE_BENCH_BACKEND")}
-    args = ["--steps", "3", "--warmup", "1", "--repeats", "2", "--width", "328", "--height", "200", "--no-cpu-baseline", "--no-other-configs", "--sustain-seconds", "0"]
+    args = ["--full", "--steps", "3", "--warmup", "1", "--repeats", "2", "--width", "328", "--height", "200", "--no-cpu-baseline", "--no-other-configs", "--sustain-seconds", "0"]
     films, lines = {}, {}
     for name, extra in (("one", ["--gpus", "1"]), ("ranks", ["--gpus", "2"]), ("group", ["--gpus", "2", "--launcher", "group"]), ("ranks3", ["--gpus", "3"]), ("ranks8", ["--gpus", "8"])):
         f = str(tmp_path / (name + ".npy"))
@@ -2096,6 +2096,30 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert lines["ranks8"]["n_gpus"] == 8 and lines["ranks8"]["ranks_seen"] == 8 and len(lines["ranks8"]["per_rank"]) == 8     # the driver's scaling command, as far as one GPU goes
     assert lines["group"]["n_gpus"] == 2 and lines["group"]["ranks_seen"] == 2 and lines["group"]["transport"] == ("copy" if shared else "rccl")
     assert lines["ranks"]["devices_seen"] == (1 if shared else 2)
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """a plain `bench.py` run (no --full) times --steps steps once and prints the headline without the --full fields; --dump-outputs writes the film those
+    steps accumulated (float32, alpha = the step count), bit for bit the same in two runs with the same arguments and the same as --dump-film's"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "328", "--height", "200"]
+    films, lines = [], []
+    for k in range(2):
+        extra = ["--dump-film", str(tmp_path / "film.npy")] if k == 0 else []
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dump-outputs", str(tmp_path / ("out%d" % k))] + extra + args,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1]))
+        films.append(np.load(tmp_path / ("out%d" % k) / "film.npy"))
+    line = lines[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == 3 and line["repeats"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"roofline", "per_rank", "sustained", "other_configs", "cpu_baseline"} & set(line)
+    f = films[0]
+    assert f.dtype == np.float32 and f.shape == (200, 328, 4) and np.isfinite(f).all() and np.all(f[..., 3] == 3.0)
+    assert np.array_equal(f.view(np.uint32), films[1].view(np.uint32))
+    assert np.array_equal(f.view(np.uint32), np.load(tmp_path / "film.npy").view(np.uint32))
 
 
 def test_subset_on_fresh_device_memory():

@@ -1,6 +1,6 @@
 # usage (on the GPU box): bash tools/profile_round.sh TAG SCENE [PASSES] [extra bench.py args]
 #   PASSES = comma list out of trace,fetch,write,sq,valu,mem,mem2 (default: all).  Kernel trace + PMC passes of
-#   `python3 bench.py --scene SCENE --no-cpu-baseline --repeats 2 ...`, each in its OWN run (gpurun refuses --pmc combined with
+#   `python3 bench.py --full --scene SCENE --no-cpu-baseline --repeats 2 ...`, each in its OWN run (--pmc is not combined with
 #   sys/hip traces; the counters of one pass have to fit the hardware's per-block limits).  MSNE_SERIAL=1: kernels in stream order, so
 #   per-kernel durations are not blurred by co-residency.  Scratch output under gpurun_out/TAG_SCENE_*; tools/profile_counters.py TAG SCENE
 #   turns it into profiles/TAG_*_SCENE.*
@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 export MSNE_SERIAL=1
 O=$R/gpurun_out/${TAG}_${SCENE}
 SC=${SCENE%_sky}; ENVARG=""; [ "$SC" != "$SCENE" ] && ENVARG="--env sky"
-ARGS="--scene $SC $ENVARG --no-cpu-baseline --no-other-configs --sustain-seconds 0 --no-gpu-visits --repeats 2 $*"
+ARGS="--full --scene $SC $ENVARG --no-cpu-baseline --no-other-configs --sustain-seconds 0 --no-gpu-visits --repeats 2 $*"
 echo "MSNE_SERIAL=1 bench.py $ARGS" > ${O}_cmd.txt
 pmc() {  # name, counters...
     n=$1; shift
