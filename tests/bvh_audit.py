@@ -337,3 +337,11 @@ def audit(bvh, scene, fresh=True, refit=False, world=None):
         for i in np.flatnonzero(item_refs != 1)[:8]:
             rep.add("I5", "TLAS", -1, -1, -1, item_refs[i], "TLAS item %d (instance %d) is referenced by %d leaf slots" % (i, items[i], item_refs[i]))
     return rep
+
+
+def assert_clean(rep, planted, what):
+    """no violation, and nothing passed over but the `planted` all-non-finite triangles"""
+    print(what, str(rep).split("\n")[0])
+    assert not rep.violations, "%s: %s" % (what, rep)
+    assert rep.skipped_leaf_slots == planted and planted <= 1 and rep.skipped_internal_slots == 0, "%s: %d leaf slots passed over, %d planted: %s" % (what, rep.skipped_leaf_slots, planted, rep)
+    assert rep.slots["I1"] > 0

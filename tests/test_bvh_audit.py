@@ -5,80 +5,16 @@ the same film.  Here every used slot of every reachable node of what MsneReadBvh
 
 The first half runs without a GPU: a small reference builder (median splits into <= 8 children, one triangle per leaf, quantised in numpy float32 from the words
 of DESIGN.md section 3) emits Node8 / TriRec bytes the auditor must pass, and single mutations of them it must report under the right invariant.  The second half
-audits what the product builds and re-fits on the GPU."""
-import os
-import subprocess
-import sys
-
+audits what the product builds and re-fits on the GPU.  Both halves and the builder-variant worker draw their soups from tests/parity_scenes.py."""
 import numpy as np
 import pytest
 
 import bvh_audit
-from bvh_audit import SceneRecorder, audit
+from bvh_audit import SceneRecorder, assert_clean, audit
+from parity_common import run_worker
+from parity_scenes import build_case, grey, soup
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-
-
-# ---------------- scenes (shared by the CPU half, the GPU half and the builder-variant worker) ----------------
-
-def soup(n, family=""):
-    """(n, 3, 3) float32 corners and the number of all-non-finite triangles planted: n random triangles, sizes spread e^N(-1.5, 1.5) (tests/test_gpu_parity.py
-    SWEEP_WORKER's soup), from 8 on with one copy pair, one triangle flat in z and one all-NaN triangle.  `family`: flat (every triangle in z = 0), far (translated
-    by 1e4 times its size), tiny / huge (times 1e-20 / 1e20), point (a triangle of three equal corners), needle (2000 : 1)."""
-    rs = np.random.default_rng(n)
-    centre = rs.normal(size=(n, 1, 3)) * 4.0
-    size = np.exp(rs.normal(size=(n, 1, 1)) * 1.5 - 1.5)
-    P = (centre + rs.normal(size=(n, 3, 3)) * size).astype(f32)
-    planted = 0
-    if family == "point":
-        P[7] = P[7, 0]
-    if family == "needle":
-        u = np.array([0.6, 0.64, 0.48]); v = np.array([-0.8, 0.48, 0.36])             # orthonormal
-        a = P[11, 0].astype(np.float64)
-        P[11, 1] = (a + 6.0 * u).astype(f32); P[11, 2] = (a + 6.0 * u + 6.0 / 2000.0 * v).astype(f32)
-    if n >= 8:
-        P[n // 2] = P[0]; P[n // 3, :, 2] = P[n // 3, 0, 2]; P[n // 5] = np.nan; planted = 1
-    if family == "flat":
-        P[..., 2] *= f32(0.0)                                                          # (NaN stays NaN)
-    if family == "far":
-        with np.errstate(invalid="ignore"):
-            size_ = float(np.nanmax(P) - np.nanmin(P))
-        P = (P.astype(np.float64) + 1.0e4 * size_ * np.array([1.0, -0.7, 0.4])).astype(f32)
-    if family == "tiny":
-        P = P * f32(1e-20)
-    if family == "huge":
-        P = P * f32(1e20)
-    return P, planted
-
-
-def grey(ctx):
-    from moonshine_amd import scenes
-    return ctx.create_material(scenes.LAMBERT, ctx.solid_texture(0.5, 0.5), ctx.solid_texture(0.0, 0.0, 0.0), color=ctx.solid_texture(0.7, 0.7, 0.7))
-
-
-def one_mesh_scene(ctx, P):
-    ctx.create_instance([(ctx.create_mesh(P.reshape(-1, 3), np.arange(3 * len(P), dtype=np.uint32).reshape(-1, 3)), grey(ctx), False)])
-    ctx.set_background(np.ones((1, 1, 4), f32), 1, 1)
-
-
-def build_case(ctx, name):
-    """a named scene into the (recording) context -> how many all-non-finite triangles it holds"""
-    from moonshine_amd import scenes
-    if name == "s2":
-        scenes.s2(ctx, extent=(16, 9), dims=(3, 3, 2), order=3)
-        return 0
-    n, _, family = name.partition("-")
-    P, planted = soup(int(n), family)
-    one_mesh_scene(ctx, P)
-    return planted
-
-
-def assert_clean(rep, planted, what):
-    print(what, str(rep).split("\n")[0])
-    assert not rep.violations, "%s: %s" % (what, rep)
-    assert rep.skipped_leaf_slots == planted and planted <= 1 and rep.skipped_internal_slots == 0, "%s: %d leaf slots passed over, %d planted: %s" % (what, rep.skipped_leaf_slots, planted, rep)
-    assert rep.slots["I1"] > 0
 
 
 # ---------------- the reference builder (CPU) ----------------
@@ -350,29 +286,14 @@ def test_gpu_degenerate_and_edge_trees(gpu_api, family):
     assert rep.slots["I2"] == rep.slots["I1"] == rep.slots["I3"] and rep.nodes_i4 == rep.nodes
 
 
-VARIANT_WORKER = r"""
-import sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-from moonshine_amd import api
-import bvh_audit, test_bvh_audit as t
-for name in ("257", "4097", "s2"):
-    rec = bvh_audit.SceneRecorder(api.Context())
-    planted = t.build_case(rec, name)
-    t.assert_clean(bvh_audit.audit(rec.read_bvh(), rec), planted, name)
-print("AUDIT_OK")
-"""
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", ["MSNE_SAH_TOP=48", "MSNE_SAH_TOP=0", "MSNE_TOPDOWN=host", "MSNE_MORTON_BITS=21"])
-def test_gpu_builder_variants(tmp_path, env):
-    """the builder's other routes (read from the environment when a context is made, hence a process of their own): PLOC, cluster rebuilds and a top tree in every
-    mesh and in the TLAS; PLOC alone; the top-down stages on the host; 63-bit Morton keys.  Soups of 257 and 4097 triangles and the instanced S2, I1-I5 each."""
-    script = tmp_path / "audit_worker.py"
-    script.write_text(VARIANT_WORKER)
+def test_gpu_builder_variants(env):
+    """the builder's other routes (read from the environment when a context is made, hence a process of their own: tests/workers/bvh_audit_variants.py): PLOC, cluster
+    rebuilds and a top tree in every mesh and in the TLAS; PLOC alone; the top-down stages on the host; 63-bit Morton keys.  Soups of 257 and 4097 triangles and the
+    instanced S2, I1-I5 each."""
     k, _, v = env.partition("=")
-    out = subprocess.run([sys.executable, str(script), ROOT], capture_output=True, text=True, timeout=300, env=dict(os.environ, MSNE_DEBUG_POISON="1", **{k: v}))
-    assert out.returncode == 0 and "AUDIT_OK" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+    run_worker("bvh_audit_variants", env={"MSNE_DEBUG_POISON": "1", k: v}, timeout=300, token="AUDIT_OK")
 
 
 @pytest.mark.gpu

@@ -13,6 +13,9 @@ import pytest
 
 from moonshine_amd import scenes
 from moonshine_amd.hostinfo import usable_cores
+from parity_common import random_rays
+from parity_scenes import random_scene
+from seeds import seeds
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -282,7 +285,7 @@ def _same_hits(c, rays, level=1):
     return bad
 
 
-@pytest.mark.parametrize("seed", __import__("seeds").seeds(list(range(24)) + [14, 501, 593, 707, 910, 1115, 1199, 1228, 2166, 2846, 3277, 3369], 60))
+@pytest.mark.parametrize("seed", seeds(list(range(24)) + [14, 501, 593, 707, 910, 1115, 1199, 1228, 2166, 2846, 3277, 3369], 60))
 def test_instance_boxes_never_change_a_hit(orc, seed):
     """The contract (orc_bvh.c:1-10) is the search over every triangle of every visible instance in ITS space; the TLAS boxes only cut it short.  They live in world space,
     and the two spaces agree up to the rounding of the inverse transform and of the transformed ray: orc_bvh.c instance_cull_slack bounds that and grows the boxes by it.
@@ -304,7 +307,7 @@ def test_instance_boxes_never_change_a_hit(orc, seed):
 
 
 @pytest.mark.parametrize("far", [1e2, 1e4, 1e6])
-@pytest.mark.parametrize("seed", __import__("seeds").seeds(list(range(6)), 6))
+@pytest.mark.parametrize("seed", seeds(list(range(6)), 6))
 def test_far_origins_with_and_without_boxes(orc, seed, far):
     """intersection.hlsl:20: any origin.  The oracle's instance slack takes the ray's origin per ray (orc_bvh.c instance_cull_slack); held here from 1e2 ... 1e6 scene
     sizes out against the search without boxes — the product's far-camera test (tests/test_gpu_parity.py::test_camera_far_outside_the_baked_reach) leans on it"""
@@ -329,18 +332,17 @@ def test_triangle_boxes_never_change_a_hit(orc):
             assert a[0] == b[0] and sa == sb and (not a[0] or (tuple(a[1]) == tuple(b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32)))), (seed, r, a, b)
 
 
-@pytest.mark.parametrize("seed", __import__("seeds").seeds(list(range(12)), 20))
+@pytest.mark.parametrize("seed", seeds(list(range(12)), 20))
 def test_no_box_changes_a_pixel(orc, seed):
-    """the randomized scenes of tests/test_gpu_parity.py rendered twice by the oracle — with its two-level BVH, and testing every triangle of every visible instance for
+    """the randomized scenes of tests/parity_scenes.py rendered twice by the oracle — with its two-level BVH, and testing every triangle of every visible instance for
     every ray (OrcSetExhaustiveSearch 2, the contract with nothing in the way): the same film bit for bit, the same ray counts, the same probe rays"""
-    import test_gpu_parity as G
     rs = np.random.default_rng(1000 + seed)
     films, counts, hits = [], [], []
-    rays = G._random_rays(200, seed, radius=8.0)
+    rays = random_rays(200, seed, radius=8.0)
     bounces = int(rs.integers(1, 5))
     for level in (0, 2):
         c = orc.Context(threads=usable_cores())
-        s, l = G._random_scene(c, seed=seed)
+        s, l = random_scene(c, seed=seed)
         c.set_pipeline(samples_per_run=1, max_bounces=bounces, env_samples_per_bounce=1, mesh_samples_per_bounce=1)
         c.set_exhaustive_search(level)
         c.render(s, l, launches=1)
@@ -354,7 +356,7 @@ def test_no_box_changes_a_pixel(orc, seed):
         assert a[0] == b[0] and sa == sb and (not a[0] or (tuple(a[1]) == tuple(b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32))))
 
 
-@pytest.mark.parametrize("seed", __import__("seeds").seeds(list(range(8)), 24))
+@pytest.mark.parametrize("seed", seeds(list(range(8)), 24))
 def test_lattice_rays_with_and_without_boxes(orc, seed):
     """exact arithmetic everywhere (tests/hull_rays.py lattice_*): rays in face planes, along edges, through corners, starting and ending on faces — box distances of
     +-0, ties between up to six triangles of several instances; the culled search against the exhaustive one"""
@@ -369,7 +371,7 @@ def test_lattice_rays_with_and_without_boxes(orc, seed):
     assert sum(1 for r in rays[:300] if c.trace_closest(r[:3], r[3:6], float(r[6]))[0]) >= 1       # (the rays do hit things; at a scale of 2^-62 as few as two of 300: seed 24871 of a 140 000-case sweep)
 
 
-@pytest.mark.parametrize("seed", __import__("seeds").seeds(list(range(6)) + [6100112, 6100853], 16))
+@pytest.mark.parametrize("seed", seeds(list(range(6)) + [6100112, 6100853], 16))
 def test_lattice_films_with_and_without_boxes(orc, seed):
     """the lattice scenes RENDERED from a camera on a lattice point, with the BVH and testing every triangle: the same film.  A camera on a face plane starts every ray
     exactly in that face's triangles' planes; the test's t for them is +-2e-8 around 0, some are taken, and the flat box of such a triangle lies exactly behind the
@@ -398,7 +400,7 @@ def test_lattice_films_with_and_without_boxes(orc, seed):
 _GRAZING_SEEDS = [6204351, 6226272, 6240180]   # round 6: a shadow ray leaving a large flat quad 1.4 degrees off its plane; the triangle test's t is +6.8e-4 around a true -2.4e-3 (box_hit8: slack per axis)
 
 
-@pytest.mark.parametrize("seed", __import__("seeds").seeds(list(range(6)) + [6200851, 6201195, 6201640] + _GRAZING_SEEDS, 16))
+@pytest.mark.parametrize("seed", seeds(list(range(6)) + [6200851, 6201195, 6201640] + _GRAZING_SEEDS, 16))
 def test_hull_films_with_and_without_boxes(orc, seed):
     """tests/test_gpu_parity.py::test_films_of_hull_and_lattice_scenes' hull family rendered by the oracle with its BVH and by its search over every triangle: the same film
     and ray counts.  Round 6's sweep of the GPU test found seed 6204351 where THIS FILE's BVH dropped an occluder the search takes (and the product too): a shadow ray that

@@ -18,8 +18,8 @@ reach = max(float(np.abs(W).max()) for W in world)
 sn = [c.create_sensor(24, 16) for c in (oc, gc)]
 rays = hull_rays.far_rays(world, seed, far)
 if "--like-the-test" in sys.argv:      # the test traces rays before it renders: the same calls in the same order
-    import test_gpu_parity as T
-    T._check_rays(oc, gc, hull_rays.hull_rays(world, seed, far=1.0)[::7]); T._check_rays(oc, gc, rays)
+    from parity_common import check_rays
+    check_rays(oc, gc, hull_rays.hull_rays(world, seed, far=1.0)[::7]); check_rays(oc, gc, rays)
 W = world[int(rs.integers(len(world)))]; ctr = 0.5 * (W.min(0) + W.max(0)); r = max(np.linalg.norm(W - ctr, axis=1).max(), 1e-20)
 eye = rs.normal(size=3); eye = eye / np.linalg.norm(eye) * reach * far * 1.7
 fwd = ctr - eye; dist = np.linalg.norm(fwd); fwd = fwd / dist
