@@ -189,6 +189,31 @@ def odd_scene(c, extent, ior, aperture):
     return c.create_sensor(*extent), lens
 
 
+def textured_scene(c, extent=(96, 64)):
+    """a sphere with vertex normals and texcoords under an sRGB colour map, a two-component normal map and a roughness map, over a grey floor, lit by the sky, seen
+    through a thin lens"""
+    rs = np.random.default_rng(7)
+    P, I = scenes.icosphere(3)
+    N = P.copy()
+    T = np.stack([np.arctan2(P[:, 1], P[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(P[:, 2], -1, 1)) / np.pi], -1).astype(np.float32)
+    mesh = c.create_mesh(P, I, normals=N, texcoords=T)
+    col = rs.integers(0, 256, size=(16, 32, 4), dtype=np.uint8)
+    nrm = (128 + rs.integers(-40, 40, size=(8, 8, 2))).astype(np.uint8)
+    rough = rs.integers(30, 200, size=(4, 4), dtype=np.uint8)
+    tcol = c.create_texture(col, 32, 16, "r8g8b8a8_srgb")
+    tn = c.create_texture(nrm, 8, 8, "r8g8_unorm")
+    tr = c.create_texture(rough, 4, 4, "r8_unorm")
+    m = c.create_material(scenes.STANDARD_PBR, tn, c.solid_texture(0.0, 0.0, 0.0), color=tcol, metalness=c.solid_texture(0.3), roughness=tr, ior=1.45)
+    c.create_instance([(mesh, m, False)])
+    gp, gi = scenes.quad((-4, -4, -1), (4, -4, -1), (4, 4, -1), (-4, 4, -1))
+    gm = grey(c, 0.6)
+    c.create_instance([(c.create_mesh(gp, gi), gm, False)])
+    img = scenes.sky_sun_equirect(64, 32)
+    c.set_background(img, 64, 32)
+    lens = c.create_lens(c.make_lens((-3, -1, 1.5), (0.8, 0.3, -0.4), (0, 0, 1), 0.7, aperture=0.05, focus_distance=3.0))
+    return c.create_sensor(*extent), lens
+
+
 def material_edit_scene(c):
     """three instances around the origin over a ground quad: [0] a transformed two-geometry instance (sphere + quad), [1] a sampled emissive quad, [2] an identity-transform
     sphere (part of the merged world BLAS, like the ground [3])"""

@@ -331,6 +331,12 @@ def incoming_radiance(sc, o, d, rng, stats=None):
         if not len(idx):
             continue
         sf = tuple(x[keep] for x in sf); tfn = tf[0][keep]; out_ss = out_ss[keep]
+        if stats is not None:
+            # MeshAttributes::inWorld (world.hlsl:166-176) normalises the three axes of a frame one by one: under a non-uniformly scaled instance the vertex and the
+            # triangle frame come out skewed, and only the texture frame is orthogonalised again (material.hlsl:498-504).  A path that scatters through one of the two
+            # fallback frames there leaves with a direction that is not of unit length, which the reference's next steps (EnvMap::eval's sqrt(1 - |z|)) are not made for.
+            skew = np.maximum(np.abs(ss.dot(sf[0], sf[1])), np.maximum(np.abs(ss.dot(sf[0], sf[2])), np.abs(ss.dot(sf[1], sf[2])))) > 1e-3
+            stats.setdefault("skewed_frame", np.zeros(n, bool))[idx[skew]] = True
         M = {k_: v_[keep] for k_, v_ in M.items()}
         delta = (M["type"] == ss.PERFECT_MIRROR) | (M["type"] == ss.GLASS)
         nd = np.flatnonzero(~delta)
@@ -361,8 +367,9 @@ def incoming_radiance(sc, o, d, rng, stats=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------- main.hlsl:43-95
-def render_launch(sc, sample_index=0):
-    """one launch at samples_per_run = 1 -> (H, W, 3) radiance of that sample (storeColor with sampleCount = 0 stores it as is)"""
+def render_launch(sc, sample_index=0, stats=None):
+    """one launch at samples_per_run = 1 -> (H, W, 3) radiance of that sample (storeColor with sampleCount = 0 stores it as is).  stats, a dict, receives
+    "skewed_frame": per pixel (row-major), whether the path scattered through a shading frame that is not orthogonal (see incoming_radiance)"""
     W, H = sc.spec["extent"]; opt = sc.opts
     assert opt["samples_per_run"] == 1
     ys, xs = np.mgrid[0:H, 0:W]; xs, ys = xs.ravel(), ys.ravel()
@@ -376,7 +383,7 @@ def render_launch(sc, sample_index=0):
     r2 = rng.get2(every)
     L = sc.spec["lens"]; b = lambda v: np.broadcast_to(np.asarray(v, np.float32).astype(np.float64), (len(xs),) + np.shape(v)).copy()
     o, d = ss.camera_generate_ray(b(L["origin"]), b(L["forward"]), b(L["up"]), b(L["vfov"]), b(L["aperture"]), b(L["focus_distance"]), float(W), float(H), uv, r2)
-    return incoming_radiance(sc, o, d, rng).reshape(H, W, 3)
+    return incoming_radiance(sc, o, d, rng, stats).reshape(H, W, 3)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the same spec into a context

@@ -17,7 +17,7 @@ import hull_rays
 from moonshine_amd import scenes
 from moonshine_amd.hostinfo import usable_cores
 from parity_common import ROOT, assert_film_equal, assert_same_bits, assert_same_ray_counts, both, check_rays, random_rays, run_worker
-from parity_scenes import edge_scene, env_image, grey, material_edit_scene, odd_scene, odd_transform_scene, pile_and_chain, random_scene
+from parity_scenes import edge_scene, env_image, grey, material_edit_scene, odd_scene, odd_transform_scene, pile_and_chain, random_scene, textured_scene
 from seeds import seeds
 
 pytestmark = pytest.mark.gpu
@@ -262,30 +262,9 @@ def test_instanced_s2_small(orc, gpu_api):
 
 def test_textured_and_normal_mapped(orc, gpu_api):
     """bilinear/repeat texture sampling, sRGB decode, two-component normal maps, vertex normals, texcoords, thin lens."""
-    rng = np.random.default_rng(7)
-    def build(c):
-        P, I = scenes.icosphere(3)
-        N = P.copy()
-        T = np.stack([np.arctan2(P[:, 1], P[:, 0]) / (2 * math.pi) + 0.5, np.arccos(np.clip(P[:, 2], -1, 1)) / math.pi], -1).astype(np.float32)
-        mesh = c.create_mesh(P, I, normals=N, texcoords=T)
-        col = rng2.integers(0, 256, size=(16, 32, 4), dtype=np.uint8)
-        nrm = (128 + rng2.integers(-40, 40, size=(8, 8, 2))).astype(np.uint8)
-        rough = rng2.integers(30, 200, size=(4, 4), dtype=np.uint8)
-        tcol = c.create_texture(col, 32, 16, "r8g8b8a8_srgb")
-        tn = c.create_texture(nrm, 8, 8, "r8g8_unorm")
-        tr = c.create_texture(rough, 4, 4, "r8_unorm")
-        m = c.create_material(scenes.STANDARD_PBR, tn, c.solid_texture(0.0, 0.0, 0.0), color=tcol, metalness=c.solid_texture(0.3), roughness=tr, ior=1.45)
-        c.create_instance([(mesh, m, False)])
-        gp, gi = scenes.quad((-4, -4, -1), (4, -4, -1), (4, 4, -1), (-4, 4, -1))
-        gm = grey(c, 0.6)
-        c.create_instance([(c.create_mesh(gp, gi), gm, False)])
-        img = scenes.sky_sun_equirect(64, 32)
-        c.set_background(img, 64, 32)
-        lens = c.create_lens(c.make_lens((-3, -1, 1.5), (0.8, 0.3, -0.4), (0, 0, 1), 0.7, aperture=0.05, focus_distance=3.0))
-        return c.create_sensor(96, 64), lens
     gc = gpu_api.Context(); oc = orc.Context(threads=8)
-    rng2 = np.random.default_rng(7); sg, lg = build(gc)
-    rng2 = np.random.default_rng(7); so, lo = build(oc)
+    sg, lg = textured_scene(gc)
+    so, lo = textured_scene(oc)
     for c in (oc, gc):
         c.set_pipeline(samples_per_run=2, max_bounces=6, env_samples_per_bounce=1, mesh_samples_per_bounce=0)
     gc.render(sg, lg, launches=2); oc.render(so, lo, launches=2)

@@ -220,7 +220,8 @@ def compare(ctx, spec, launches=2, strict=True):
         ctx.render(sensor, lens, launches=1)
         film = ctx.sensor_data(sensor)[..., :3].astype(np.float64)
         got = film if k == 0 else film * (k + 1) - before * k
-        ref = ssr.render_launch(sc, sample_index=k)
+        stats = {}
+        ref = ssr.render_launch(sc, sample_index=k, stats=stats)
         # a pixel either follows the same path as the restatement — then it differs by f32 rounding, amplified where the formulas are ill-conditioned
         # (the rescaled random numbers of the mip descent, GGX's D near its peak, bilinear weights): up to a few 1e-3 on single pixels — or a decision
         # flipped somewhere along it and the sample is a different one altogether
@@ -232,7 +233,12 @@ def compare(ctx, spec, launches=2, strict=True):
         rel = float(np.linalg.norm(got[same] - ref[same]) / max(np.linalg.norm(ref[same]), 1e-300))      # (a black image: both must be black)
         report.append(dict(sample=k, pixels=int(finite.sum()), diverged=int(diverged.sum()), beyond_1e4=int((same & (err > 1e-4)).sum()), rel_l2=rel,
                            mean_ratio=float(got[finite].mean() / ref[finite].mean()) if ref[finite].mean() != 0 else (1.0 if got[finite].mean() == 0 else float("inf"))))
-        assert finite.mean() > (0.995 if strict else 0.98), report
+        # a pixel that is not finite on BOTH sides and whose path scattered through a skewed frame is ill-posed in the reference itself (seed 482751: a normal-mapped
+        # mirror quad on a non-uniformly scaled instance seen at a grazing angle, 3 % of the image; the reference's own HLSL gives NaN there too): it is not held
+        # against the guard.  Anything else that is not finite is.
+        ill_posed = ~np.isfinite(ref).all(-1) & ~np.isfinite(got).all(-1) & stats.get("skewed_frame", np.zeros(finite.size, bool)).reshape(finite.shape)
+        report[-1]["ill_posed"] = int(ill_posed.sum())
+        assert (finite | ill_posed).mean() > (0.995 if strict else 0.98), report
         assert diverged.mean() <= 0.01, "sample %d: %.2f %% of the paths diverge from the float64 restatement: %s" % (k, 100 * diverged.mean(), report)
         assert (same & (err > 1e-4)).mean() <= 0.03, report
         assert rel < (1e-4 if strict else 1e-3), report            # north_star: relative per-pixel L2 below 1e-4
@@ -243,7 +249,7 @@ def compare(ctx, spec, launches=2, strict=True):
 
 def _random_seeds(rotating=0):
     from seeds import seeds
-    return seeds(list(range(6)), rotating)
+    return seeds(list(range(6)) + [482751], rotating)     # 482751: the ill-posed pixels of compare()
 
 
 @pytest.mark.parametrize("seed", _random_seeds())
