@@ -534,6 +534,37 @@ def vk_sample_linear(img, uv, mirrored=False):
     return (1 - a) * (1 - b) * img[y0, x0] + a * (1 - b) * img[y0, x1] + (1 - a) * b * img[y1, x0] + a * b * img[y1, x1]
 
 
+# ------------------------------------------------------------------ what a texel of a vk.Format IS, before any filtering
+# Written from the Vulkan specification's format definitions ("Formats": "Conversion from Normalized Fixed-Point to Floating-Point" f = c / (2^b - 1);
+# "sRGB EOTF" applied to the R, G and B components of an _SRGB format and not to A; "16-Bit Floating-Point Numbers" = IEEE 754 binary16;
+# "Conversion Formats / Component Substitution": a component the format lacks reads 0 for G and B, 1 for A) and from vkCmdCopyBufferToImage
+# with bufferRowLength = 0 (rows tightly packed), which is how MaterialManager.zig:351-390 uploads every texture.  Not from csrc/msne_device.h.
+TEXEL_FORMATS = {"r8g8b8a8_srgb": (4, np.uint8), "r8g8_unorm": (2, np.uint8), "r8_unorm": (1, np.uint8), "r32g32b32a32_sfloat": (4, np.float32),
+                 "r32g32_sfloat": (2, np.float32), "r32_sfloat": (1, np.float32), "r16g16b16a16_sfloat": (4, np.uint16)}     # name -> (components, storage type; halves as their bits)
+
+
+def srgb_eotf(x):
+    return np.where(x <= 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4)
+
+
+def decode_texels(raw, w, h, format):
+    """the bytes of a w x h image in a vk.Format (any array whose memory is those bytes, row after row) -> (h, w, 4) float64"""
+    n, dt = TEXEL_FORMATS[format]
+    c = np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=dt, count=w * h * n).reshape(h, w, n)
+    if format == "r8g8b8a8_srgb":
+        x = c.astype(np.float64) / 255.0
+        c = np.concatenate([srgb_eotf(x[..., :3]), x[..., 3:]], -1)
+    elif dt == np.uint8:
+        c = c.astype(np.float64) / 255.0
+    elif dt == np.uint16:
+        c = c.view(np.float16).astype(np.float64)
+    else:
+        c = c.astype(np.float64)
+    out = np.zeros((h, w, 4)); out[..., 3] = 1.0
+    out[..., :n] = c
+    return out
+
+
 def fold_pyramid(level0):
     """shaders/background/fold.hlsl: each level is the 2x2 SUM of the one below"""
     out = [_a(level0)]

@@ -81,8 +81,17 @@ def alias_table(weights):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the scene
+def texture_image(t):
+    """a spec texture -> the (h, w, 4) float64 image a lookup filters: a plain HxWx4 float array as it is; a (raw array of shape (h, w, ...), vk.Format name)
+    pair decoded from the format's definition (second_source.decode_texels).  A module-level name so that a test can show the comparison notices another decoder."""
+    if isinstance(t, tuple):
+        raw, fmt = t
+        return ss.decode_texels(raw, raw.shape[1], raw.shape[0], fmt)
+    return np.asarray(t, np.float64)
+
+
 class Scene:
-    """spec: dict(textures=[HxWx4 float arrays], materials=[dict(type, normal, emissive, color, metalness, roughness, ior)],
+    """spec: dict(textures=[HxWx4 float arrays, or (raw texels, format name) pairs: texture_image], materials=[dict(type, normal, emissive, color, metalness, roughness, ior)],
     meshes=[dict(positions, indices, normals=None, texcoords=None)], instances=[dict(transform=3x4 or None, geometries=[(mesh, material, sampled)])],
     lens=dict(origin, forward, up, vfov, aperture, focus_distance), extent=(W, H), opts=dict(...)); env: second_source.EnvMap"""
 
@@ -138,7 +147,7 @@ class Scene:
             self.alias_tri = np.array([first_of[(i, g)] + k for (i, g, k) in wdata], int)
         else:
             self.alias, self.select, self.alias_sum, self.alias_tri = np.zeros(0, np.uint32), np.zeros(0, np.float32), np.float32(0), np.zeros(0, int)
-        self.textures = [np.asarray(t, np.float64) for t in spec["textures"]]
+        self.textures = [texture_image(t) for t in spec["textures"]]
 
     @staticmethod
     def _mul_point32(m, p):   # vector.zig Mat3x4.mul_point in f32: row . (p, 1), summed left to right
@@ -389,7 +398,12 @@ def render_launch(sc, sample_index=0, stats=None):
 # ---------------------------------------------------------------------------------------------------------------- the same spec into a context
 def build_context(ctx, spec):
     """pushes the spec through the C ABI of a context (moonshine_amd.api.Context or the oracle's) -> (sensor, lens)"""
-    tex = [ctx.create_texture(np.ascontiguousarray(t, np.float32), t.shape[1], t.shape[0], "r32g32b32a32_sfloat") for t in spec["textures"]]
+    def upload(t):      # a (raw texels, format) pair goes over in that format, untouched; a plain float image as float RGBA
+        if isinstance(t, tuple):
+            raw, fmt = t
+            return ctx.create_texture(np.ascontiguousarray(raw), raw.shape[1], raw.shape[0], fmt)
+        return ctx.create_texture(np.ascontiguousarray(t, np.float32), t.shape[1], t.shape[0], "r32g32b32a32_sfloat")
+    tex = [upload(t) for t in spec["textures"]]
     mats = [ctx.create_material(m["type"], tex[m["normal"]], tex[m["emissive"]], color=tex[m["color"]], metalness=tex[m["metalness"]],
                                 roughness=tex[m["roughness"]], ior=m["ior"]) for m in spec["materials"]]
     meshes = [ctx.create_mesh(np.asarray(m["positions"], np.float32), np.asarray(m["indices"], np.uint32), normals=m.get("normals"), texcoords=m.get("texcoords")) for m in spec["meshes"]]

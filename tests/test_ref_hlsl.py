@@ -26,7 +26,7 @@ from tests import test_second_source as tss
 from tests.parity_scenes import env_image, odd_scene, textured_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROBES = [n for n in tss.STATELESS + tss.ENV if n != "texture"]        # 17, the bare texture sample, would test the shim's sampler
+PROBES = [n for n in tss.STATELESS + tss.ENV if n != "texture"]        # 17, the bare texture sample, would test the shim's sampler (tests/test_second_source_textures.py judges it by the Vulkan definitions)
 ENVIRONMENTS = ["sky", "odd_size", "two_by_one", "hot_pixel", "black", "tall"]
 THREADS = 8
 

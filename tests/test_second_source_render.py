@@ -198,11 +198,52 @@ def spec_random(seed):
                           indexed_attributes=not hydra, two_component_normal_texture=not hydra, flip_image=bool(rs.random() < 0.5) if hydra else True))
 
 
-SPECS = {"mixed": spec_mixed, "textured": spec_textured, "hydra_mode": lambda: spec_textured(indexed=False, two_component=False, env_n=1, mesh_n=1), "lights": spec_lights}
+def spec_formats(constant=False):
+    """spec_textured's layout with every image texture in the format the GLB importer produces for its role (sRGB colour, r8g8_unorm normal map, r8_unorm metalness)
+    or in one of the remaining formats, handed over as RAW texels (second_source_render.texture_image decodes them from the format's definition), in awkward shapes:
+    odd widths, a 7x1 strip, a 15-byte texture; plus a half-float emissive image on a quad sampled as a mesh light (the descriptor copy inside LightTri).  This is
+    k_shade's own use of the formats: prefetched descriptors, per-format pool offsets.  The background is a dim random image, not the sun+sky: compare() scales errors
+    by the image mean, and a bright sun hides dim pixels.
+    constant: every texture cut to its top-left texel, 1x1 in the same format — the scene renders through k_shade<TEX = false> and the host-decoded TexDesc::first."""
+    rs = np.random.default_rng(11)
+    col = (rs.integers(40, 240, (7, 13, 4), dtype=np.uint8), "r8g8b8a8_srgb")
+    nrm = ((128 + rs.integers(-50, 50, (3, 9, 2))).astype(np.uint8), "r8g8_unorm")
+    metal = (rs.integers(0, 256, (5, 3), dtype=np.uint8), "r8_unorm")
+    rough = (rs.uniform(0.3, 0.95, (4, 6)).astype(np.float32), "r32_sfloat")
+    nrm2 = ((0.5 + rs.uniform(-0.2, 0.2, (5, 5, 2))).astype(np.float32), "r32g32_sfloat")
+    em = (rs.uniform(0.5, 9.0, (4, 4, 4)).astype(np.float16).view(np.uint16), "r16g16b16a16_sfloat")
+    col2 = (rs.uniform(0.2, 0.9, (1, 7, 4)).astype(np.float16).view(np.uint16), "r16g16b16a16_sfloat")
+    textures = [nrm, _tex(0, 0, 0), col, metal, rough, nrm2, col2, em, _tex(0.5, 0.5, 1.0), _tex(0.6, 0.6, 0.6), _tex(0.0), _tex(0.5)]
+    if constant:
+        textures = [(np.ascontiguousarray(t[0][:1, :1]), t[1]) if isinstance(t, tuple) else t for t in textures]
+    materials = [dict(type=ss.STANDARD_PBR, normal=0, emissive=1, color=2, metalness=3, roughness=4, ior=1.5),
+                 dict(type=ss.LAMBERT, normal=5, emissive=1, color=6, metalness=1, roughness=1, ior=1.5),
+                 dict(type=ss.LAMBERT, normal=8, emissive=7, color=1, metalness=10, roughness=11, ior=1.5),
+                 dict(type=ss.LAMBERT, normal=8, emissive=1, color=9, metalness=10, roughness=11, ior=1.5)]
+    P, I = scenes.icosphere(1)
+    sphere = dict(positions=P, indices=I, normals=(P / np.linalg.norm(P, axis=1, keepdims=True)).astype(np.float32),
+                  texcoords=(np.stack([np.arctan2(P[:, 1], P[:, 0]) / (2 * math.pi) + 0.5, np.arccos(np.clip(P[:, 2], -1, 1)) / math.pi], -1) * 2.5 - 0.7).astype(np.float32))
+    floor = _quad_mesh((-3, -3, 0), (3, -3, 0), (3, 3, 0), (-3, 3, 0), uv=True); floor["texcoords"] = (floor["texcoords"] * 2.3 - 0.6).astype(np.float32)
+    light = _quad_mesh((-1, -1, 0), (1, -1, 0), (1, 1, 0), (-1, 1, 0), uv=True)
+    inst = [dict(transform=None, geometries=[(1, 1, False)]), dict(transform=_xf(_rot((0.3, 1, 0.2), 0.5) * 1.1, (0.1, 0.2, 1.2)), geometries=[(0, 0, False)]),
+            dict(transform=_xf(np.eye(3) * 0.5, (1.6, -1.2, 0.5)), geometries=[(0, 3, False)]),
+            dict(transform=_xf(_rot((1, 0, 0), math.pi) * 0.8, (-0.5, 0.5, 3.2)), geometries=[(2, 2, True)])]       # the light, facing down, sampled
+    bg = np.zeros((4, 8, 4), np.float32); bg[..., :3] = rs.uniform(0.3, 0.9, (4, 8, 3)); bg[..., 3] = 1
+    return dict(textures=textures, materials=materials, meshes=[sphere, floor, light], instances=inst, background=bg,
+                lens=dict(origin=(-3.6, -3.0, 2.4), forward=tuple(np.float32(np.array([3.6, 3.0, -1.7]) / np.linalg.norm([3.6, 3.0, -1.7]))), up=(0, 0, 1), vfov=0.75, aperture=0.0, focus_distance=1.0),
+                extent=(48, 36), opts=dict(max_bounces=4, env_samples_per_bounce=1, mesh_samples_per_bounce=1))
+
+
+def spec_formats_constant():
+    return spec_formats(constant=True)
+
+
+SPECS = {"mixed": spec_mixed, "textured": spec_textured, "hydra_mode": lambda: spec_textured(indexed=False, two_component=False, env_n=1, mesh_n=1), "lights": spec_lights,
+         "formats": spec_formats, "formats_constant": spec_formats_constant}
 
 
 def compare(ctx, spec, launches=2, strict=True):
-    """strict: the thresholds of the four hand-made scenes.  Scenes drawn from seeds are 400-1700 pixels small and one bright ill-conditioned pixel moves their relative
+    """strict: the thresholds of the hand-made scenes (SPECS).  Scenes drawn from seeds are 400-1700 pixels small and one bright ill-conditioned pixel moves their relative
     L2 and their mean: for them the typical pixel is held to 1e-5 (median), the image to 1e-3, the mean to 5 % (5200 seeds: 13 beyond the strict thresholds, all by
     one to four pixels, worst relative L2 4.7e-4)"""
     sensor, lens = ssr.build_context(ctx, spec)
@@ -292,10 +333,55 @@ def test_alias_table_restatement_is_a_distribution():
     assert np.allclose(p, w / w.sum(), rtol=1e-5, atol=1e-7) and abs(float(total) - float(w.sum())) < 1e-4
 
 
-@pytest.mark.parametrize("mutation", ["float2_order", "no_face_forward", "rr_one_bounce_early", "light_sample_count_in_mis"])
+def _srgb_bytes_as(curve):
+    def f(raw, img):
+        out = img.copy(); out[..., :3] = curve(raw[..., :3] / 255.0)
+        return out
+    return f
+
+
+def _r8_rows_at_pitch_4(raw, img):      # the uploader pads every row to 4 bytes, the reader takes them tightly packed
+    h, w = raw.shape
+    return ss.decode_texels(np.pad(raw, ((0, 0), (0, -w % 4))).reshape(-1)[:w * h], w, h, "r8_unorm")
+
+
+# decoders that are wrong for ONE texture of spec_formats, named by (format, (h, w)): raw texels, the right image -> the wrong image
+DECODER_MUTATIONS = {
+    "rg8_normal_channels_swapped": ("r8g8_unorm", (3, 9), lambda raw, img: img[..., [1, 0, 2, 3]]),
+    "rg8_normal_divided_by_256": ("r8g8_unorm", (3, 9), lambda raw, img: img * [255.0 / 256.0, 255.0 / 256.0, 1, 1]),
+    "r8_metalness_divided_by_256": ("r8_unorm", (5, 3), lambda raw, img: img * [255.0 / 256.0, 1, 1, 1]),
+    "r8_rows_padded_to_4_bytes": ("r8_unorm", (5, 3), _r8_rows_at_pitch_4),
+    "srgb_as_gamma_2.2": ("r8g8b8a8_srgb", (7, 13), _srgb_bytes_as(lambda x: x ** 2.2)),
+    "srgb_read_as_unorm": ("r8g8b8a8_srgb", (7, 13), _srgb_bytes_as(lambda x: x)),
+    "half_emissive_scaled_by_1_plus_2^-7": ("r16g16b16a16_sfloat", (4, 4), lambda raw, img: img * (1.0 + 2.0 ** -7)),
+    "half_colour_shifted_one_texel": ("r16g16b16a16_sfloat", (1, 7), lambda raw, img: np.roll(img, 1, 1)),
+    "r32_roughness_shifted_one_texel": ("r32_sfloat", (4, 6), lambda raw, img: np.roll(img, 1, 1)),
+    "rg32_normal_channels_swapped": ("r32g32_sfloat", (5, 5), lambda raw, img: img[..., [1, 0, 2, 3]]),
+}
+
+
+@pytest.mark.parametrize("mutation", ["float2_order", "no_face_forward", "rr_one_bounce_early", "light_sample_count_in_mis"] + list(DECODER_MUTATIONS))
 def test_comparison_catches_mutations_of_the_restatement(orc, monkeypatch, mutation):
     """the pixel-by-pixel comparison is sensitive: a restatement that consumes the two floats of a float2 in the other order, offsets the next ray along the
-    unflipped normal, starts Russian roulette one bounce early or forgets the light-sample count in the MIS weight no longer matches the oracle"""
+    unflipped normal, starts Russian roulette one bounce early or forgets the light-sample count in the MIS weight no longer matches the oracle — nor does one
+    that decodes a single texture of spec_formats wrongly (DECODER_MUTATIONS: a swapped channel, / 256, a row pitch, another transfer curve, halves scaled by
+    1 + 2^-7, a texel shift)"""
+    if mutation in DECODER_MUTATIONS:
+        fmt, shape, wrong = DECODER_MUTATIONS[mutation]
+        real = ssr.texture_image
+        hit = []
+
+        def texture_image(t):
+            img = real(t)
+            if isinstance(t, tuple) and t[1] == fmt and t[0].shape[:2] == shape:
+                hit.append(mutation)
+                return np.asarray(wrong(t[0], img), np.float64)
+            return img
+        monkeypatch.setattr(ssr, "texture_image", texture_image)
+        with pytest.raises(AssertionError):
+            compare(orc.Context(threads=8), spec_formats(), launches=1)
+        assert hit == [mutation]          # (exactly one texture was decoded wrongly, and compare() got that far)
+        return
     if mutation == "float2_order":
         def get2(self, idx):
             b = self.get(idx); a = self.get(idx)
